@@ -2,6 +2,8 @@
 import json
 import os
 
+import pytest
+
 import bench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -110,3 +112,86 @@ def test_issue_budget_classes():
     assert c("v_exp_f32 v58, v61") == "trans" and c("v_rcp_f32 v119, v114") == "trans"
     assert c("v_mov_b32_dpp v82, v68 row_ror:8 row_mask:0xf bank_mask:0xf bound_ctrl:1") == "dpp"
     assert c("ds_read_b128 v[26:29], v52 offset:1056") == "lds" and c("s_waitcnt lgkmcnt(0)") == "wait" and c("s_and_b64 s[8:9], vcc, s[8:9]") == "salu"
+
+
+def test_dump_outputs_are_float32_sampled_and_bounded(tmp_path):
+    """`bench.py --dump-outputs DIR`: images whole, per-Gaussian arrays as one fixed seeded sample of rows (the same rows in every
+    array and every run), float32 on disk, all files together within DUMP_LIMIT_BYTES -- also when the images alone exceed it."""
+    import numpy as np
+    import torch
+    N = bench.DUMP_ROWS + 1000
+    g = torch.Generator().manual_seed(0)
+    imgs = dict(color=torch.rand(3, 64, 48, generator=g), alpha=torch.rand(1, 64, 48, generator=g, dtype=torch.float64))
+    per = dict(radii=torch.randint(0, 50, (N,), generator=g, dtype=torch.int32), grad_shs=torch.rand(N, 16, 3, generator=g),
+               grad_means2D_views=torch.rand(2, N, 3, generator=g))
+    names = bench.dump_outputs(str(tmp_path / "a"), imgs, per, N)
+    bench.dump_outputs(str(tmp_path / "b"), imgs, per, N)
+    assert names == ["alpha", "color", "gaussian_rows", "grad_means2D_views", "grad_shs", "radii"]
+    load = lambda d, k: np.load(str(tmp_path / d / (k + ".npy")))
+    rows = load("a", "gaussian_rows").astype(np.int64)
+    assert len(rows) == bench.DUMP_ROWS and np.all(np.diff(rows) > 0) and rows[-1] < N
+    assert load("a", "color").dtype == np.float32 and load("a", "alpha").dtype == np.float64
+    assert np.array_equal(load("a", "color"), imgs["color"].numpy())
+    assert load("a", "radii").dtype == np.float32 and np.array_equal(load("a", "radii"), per["radii"][rows].float().numpy())
+    assert np.array_equal(load("a", "grad_shs"), per["grad_shs"][rows].numpy())
+    assert np.array_equal(load("a", "grad_means2D_views"), per["grad_means2D_views"][:, rows].numpy())
+    for k in names:
+        assert np.array_equal(load("a", k), load("b", k)), k
+    big = dict(color=torch.rand(4, 3, 1024, 1024, generator=g))             # 50 MB of images + the sampled rows: over the limit
+    bench.dump_outputs(str(tmp_path / "c"), big, per, N)
+    assert sum(f.stat().st_size for f in (tmp_path / "c").iterdir()) <= bench.DUMP_LIMIT_BYTES
+    idx = load("c", "color.sample").astype(np.int64)
+    assert np.array_equal(load("c", "color"), big["color"].numpy().reshape(-1)[idx])
+
+
+_GRADS = ["grad_means3D", "grad_opacities", "grad_rotations", "grad_scales", "grad_shs"]
+_IMAGES = ["alpha", "color", "depth"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("extra, files", [
+    ([], _IMAGES + _GRADS + ["grad_means2D", "radii"]),
+    (["--activations", "fused"], _IMAGES + ["grad_means2D", "grad_means3D", "grad_opacity", "grad_rotation", "grad_scaling", "grad_shs", "radii"]),
+    (["--views", "2"], _IMAGES + _GRADS + ["grad_means2D", "radii"]),
+    (["--views", "2", "--views-serial"], [f"{k}_view{i}" for k in ("alpha", "color", "depth") for i in (0, 1)] + _GRADS
+     + ["grad_means2D_view0", "grad_means2D_view1", "radii_view0", "radii_view1"]),
+    (["--step", "sds", "--sds-mode", "local", "--sds-workload", "5k-256-sh0"], _IMAGES + _GRADS + ["grad_means2D", "radii"]),
+], ids=["render", "activations-fused", "views-batched", "views-serial", "sds-local"])
+def test_bench_run_dumps_what_its_step_computes(gpu, tmp_path, extra, files):
+    """`bench.py --dump-outputs` end to end on the 5k workload: which arrays main() / run_sds() capture in each step kind, and --
+    for the plain render step -- that they are what one direct call of the rasterizer with the same seeded inputs returns (the
+    run takes the bit-reproducible backward, so the direct call does too)."""
+    import subprocess
+    import sys
+    import numpy as np
+    import torch
+    import dreamgaussian_amd as D
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "5k-256-sh0", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(out)] + extra
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
+    assert line["steps"] == 2 and line["config"]["deterministic_backward"] is True
+    assert sorted(f[:-4] for f in os.listdir(out)) == sorted(files)
+    got = {f[:-4]: np.load(str(out / f)) for f in os.listdir(out)}
+    assert all(x.dtype == np.float32 and np.isfinite(x).all() for x in got.values())
+    if extra:
+        return
+    wl = bench.WORKLOADS["5k-256-sh0"]
+    sc, _, rs, grads = bench.build_inputs(wl, "blob", gpu, 0.0)
+    t = {k: v.to(gpu).requires_grad_(True) for k, v in sc.items()}
+    m2d = torch.zeros(wl["N"], 3, device=gpu, requires_grad=True)
+    old = D.set_deterministic(True)
+    try:
+        color, radii, depth, alpha = D.GaussianRasterizer(raster_settings=rs)(
+            means3D=t["means3D"], means2D=m2d, shs=t["shs"], colors_precomp=None, opacities=t["opacities"], scales=t["scales"],
+            rotations=t["rotations"], cov3D_precomp=None)
+        torch.autograd.backward([color, depth, alpha], [g.to(gpu) for g in grads])
+    finally:
+        D.set_deterministic(old)
+    want = dict(color=color, depth=depth, alpha=alpha, radii=radii, grad_means2D=m2d.grad, **{"grad_" + k: v.grad for k, v in t.items()})
+    for k, v in want.items():
+        v = v.detach().float().cpu().numpy()
+        assert got[k].shape == v.shape, k
+        assert np.abs(got[k] - v).max() <= 1e-6 * np.abs(v).max() + 1e-12, k
